@@ -72,7 +72,17 @@ def parse_args(argv=None):
     ap.add_argument("--dump-records", default=None,
                     help="rank 0 writes every call's (global id, logp, summary), gathered from all ranks after the timed "
                          "region, to this .npz (parity of an N-rank run with a 1-rank run: tests/test_gpu_parity.py)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the timed path computed in its LAST step -- every call's "
+                         "log-probability and path summary, gathered from all ranks, in global call order -- as DIR/call_id.npy, "
+                         "DIR/logp.npy and DIR/summary.npy (float64; at most 64 MB in all, a fixed seeded sample of the calls "
+                         "beyond that).  The inputs are seeded: the same arguments give the same inputs on every run and build")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the line is a rate over the timed steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def emulation_argv(argv, n):

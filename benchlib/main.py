@@ -11,6 +11,7 @@ from .hostinfo import HostRegion, cpu_quota_cores
 from .common import (CLOCK_GHZ, HBM_PEAK_GBPS, SIMDS, algorithmic_bytes, cpu_baseline, cpu_model_name, load_json,
                      measured_clock_ghz, pmc_section, ru_concordance)
 from .illumina import illumina_pipeline_input, illumina_pipeline_record, target_configuration_records
+from .outputs import write_outputs
 from .passes import Passes, passes_of, two_in_flight_ms
 from .records import forward_record, s300_record
 from .rehearsal import scale_rehearsal
@@ -248,6 +249,8 @@ def main(argv=None):
     host_region.__exit__(None, None, None)
     host_rec = host_region.record()
     elapsed = comm.allreduce_max(elapsed_mine) if comm else elapsed_mine
+    # what the last timed step computed, fetched from the copy of the batch that ran it (every pass of the region has finished)
+    last_step = passes.last.fetch() if args.dump_outputs else None
 
     # one more pass outside the timed region whose gathered records rank 0 checks against what its engine holds
     gathered = (None, None)
@@ -283,15 +286,22 @@ def main(argv=None):
         if workload in ("c3", "c4"):
             assert sum(counts) == total_calls, (sum(counts), total_calls)
 
-    if args.dump_records:
+    def global_ids():
         if workload in ("c3", "c4"):                        # global call id = position in the whole set's locus order
             first = np.concatenate([[0], np.cumsum([p[0] for p in plan])])
-            ids = np.concatenate([np.arange(first[int(k)], first[int(k) + 1]) for k in mine]) if len(mine) else np.zeros(0, np.int64)
-        else:
-            ids = np.arange(n_reads, dtype=np.int64) + rank * n_reads
+            return np.concatenate([np.arange(first[int(k)], first[int(k) + 1]) for k in mine]) if len(mine) else np.zeros(0, np.int64)
+        return np.arange(n_reads, dtype=np.int64) + rank * n_reads
+
+    if args.dump_records:
+        ids = global_ids()
         res = sharding.gather_records(comm, ids, logp, summ) if comm else (ids, logp, summ)
         if rank == 0:
             np.savez(args.dump_records, ids=res[0], logp=res[1], summary=res[2])
+    if args.dump_outputs:
+        ids = global_ids()
+        res = sharding.gather_records(comm, ids, *last_step) if comm else (ids,) + tuple(last_step)
+        if rank == 0:
+            write_outputs(args.dump_outputs, *res)
 
     # ---------------------------------------------------------------- the line's own N = 1 baseline
     # An N-rank strong-scaling line is only worth its same-workload one-rank rate: rank 0 scores the WHOLE set alone, here, after
@@ -477,7 +487,13 @@ def main(argv=None):
                                              "throttled_usec": mt_host.get("throttled_usec_delta"),
                                              "sample": "first %d reads, oracle/viterbi_oracle.c on %d pthreads (= the CPU quota of the "
                                                        "process's control group); GPU logp bit-equal on the sample" % (n_mt, cores)}
-        emit(order_line(out))
+        line = order_line(out)
+        if workload == "c1":
+            line, sub = split_line(line)
+            if sub:
+                sys.stderr.write(json.dumps({"sub_records": sub}) + "\n")
+                sys.stderr.flush()
+        emit(line)
     passes.close()
     if comm:
         comm.close()
@@ -581,3 +597,19 @@ def order_line(out):
         if k in out:
             ordered[k] = out[k]
     return ordered
+
+
+# The C1 line's records of the other configurations (20 KB together, more than a driver that keeps a bounded tail of stdout
+# holds): `summary` condenses them on the line, and they are written whole to stderr as one JSON line {"sub_records": {...}}
+SUB_RECORDS = ("s300", "log_probability", "c2", "end_to_end", "illumina_pipeline", "c4", "pacbio_end_to_end", "prefilter",
+               "flank_align", "scale_rehearsal", "c4_scale_rehearsal")
+
+
+def split_line(line):
+    """(the line without its sub-records, naming where they went; the sub-records, or None when it has none)."""
+    sub = {k: line[k] for k in SUB_RECORDS if k in line}
+    if not sub:
+        return line, None
+    head = {k: v for k, v in line.items() if k not in sub}
+    head["sub_records"] = {"keys": list(sub), "where": "stderr: one JSON line {\"sub_records\": {...}}"}
+    return head, sub

@@ -16,6 +16,7 @@ class Passes(object):
         # streams of one class can land on the same hardware queue, where their kernels would run strictly one after the other
         self.batches = [make(SECOND_QUEUE if i else 0) for i in range(max(1, int(in_flight)))]
         self.k = 0
+        self.last = None          # the copy that ran the latest pass (its results are that pass's)
 
     def run(self, reserve=0):
         b = self.batches[self.k % len(self.batches)]
@@ -23,6 +24,7 @@ class Passes(object):
         if reserve:
             b.reserve_next(reserve)
         b.run()
+        self.last = b
         return b
 
     def sync(self):

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 from conftest import ROOT
 
 
@@ -129,6 +132,97 @@ def test_line_order_summary_first_bulky_records_last():
                                                   {"loop_ms": 11.6, "kernel_ms": 10.9, "gather_ms": 0.7, "host": {"nr_throttled_delta": 2}}]}})
     assert multi["efficiency_measured"] == 0.85 and multi["same_workload_n1_value"] == 11.7e6
     assert multi["slowest_rank_loop_ms"] == 11.6 and multi["max_gather_ms"] == 0.7 and multi["throttled_periods_in_timed_region"] == 2
+
+
+def test_c1_line_fits_a_bounded_tail_with_its_sub_records_apart():
+    """The C1 line with every sub-record (the committed driver-flags line, 20 KB) is split: the stdout line keeps `summary` first,
+    the contract's keys and the summary of the sub-records, in under 8 KB; the sub-records themselves go apart, whole."""
+    from benchlib.main import SUB_RECORDS, split_line
+    d = json.load(open(os.path.join(ROOT, "profiles", "r06_c1_bench_driver_flags.json")))
+    line, sub = split_line(d)
+    assert len(json.dumps(line)) < 8000 and list(line)[0] == "summary" and line["summary"] == d["summary"]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert line[k] == d[k], k
+    assert set(sub) == {k for k in SUB_RECORDS if k in d} and all(sub[k] == d[k] for k in sub)
+    assert line["sub_records"]["keys"] == list(sub) and not set(sub) & set(line)
+    assert set(line) | set(sub) == set(d) | {"sub_records"}
+    assert split_line({"summary": {}, "metric": "m"}) == ({"summary": {}, "metric": "m"}, None)
+
+
+def _files(tree):
+    out = {}
+    for d, dirs, files in os.walk(tree):
+        dirs[:] = [x for x in dirs if x != "__pycache__" and os.path.join(d, x) != os.path.join(tree, "oracle", "_ref")]
+        for f in files:
+            if f == ".build.lock" and d == tree:                 # (root may still write a read-only tree: the lock is not a product)
+                continue
+            st = os.stat(os.path.join(d, f))
+            out[os.path.relpath(os.path.join(d, f), tree)] = (st.st_size, st.st_mtime_ns)
+    return out
+
+
+def test_bench_runs_in_a_built_tree_it_cannot_write(tmp_path):
+    """A built tree copied without its files' times (a built library may now look older than its sources) and then made
+    read-only, as when the one who runs the bench is not the one who built: build() rebuilds and writes nothing there (its
+    lock goes to the temporary directory), and bench.py runs."""
+    import hashlib
+    import shutil
+    import tempfile
+    tree = str(tmp_path / "tree")
+    shutil.copytree(ROOT, tree, copy_function=shutil.copy,
+                    ignore=shutil.ignore_patterns(".git", "__pycache__", ".build.lock"))
+    before = _files(tree)
+    lock = os.path.join(tempfile.gettempdir(), "advntr_build_%d_%s.lock" % (os.getuid(), hashlib.sha256(tree.encode()).hexdigest()[:16]))
+    paths = [d for d, _, _ in os.walk(tree)] + [os.path.join(d, f) for d, _, fs in os.walk(tree) for f in fs]
+    for p in paths:
+        os.chmod(p, os.stat(p).st_mode & ~0o222)
+    try:
+        p = subprocess.run([sys.executable, os.path.join(tree, "bench.py"), "--dry-run"], cwd=tree, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, timeout=300)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        assert _line(p.stdout)["dry_run"] is True
+        assert _files(tree) == before
+    finally:
+        for p in paths:
+            os.chmod(p, os.stat(p).st_mode | 0o200)
+        if os.path.exists(lock):
+            os.unlink(lock)
+
+
+def test_steps_and_warmup_are_checked():
+    from benchlib.cli import parse_args
+    a = parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "d"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--steps", "-1"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            parse_args(bad)
+
+
+def test_dump_outputs_files_budget_and_sample(tmp_path):
+    """--dump-outputs writes float64 .npy files in global call order; beyond the byte budget, a fixed seeded sample of the calls."""
+    from benchlib.outputs import write_outputs
+    rng = np.random.default_rng(1)
+    n = 5000
+    ids = rng.permutation(n)
+    logp = -rng.random(n) * 100
+    summ = rng.integers(0, 1000, (n, 8)).astype(np.int32)
+    shapes = write_outputs(str(tmp_path / "all"), ids, logp, summ)
+    assert shapes == {"call_id": (n,), "logp": (n,), "summary": (n, 8)}
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in shapes}
+    assert all(a.dtype == np.float64 for a in got.values())
+    order = np.argsort(ids)
+    assert np.array_equal(got["call_id"], np.arange(n)) and np.array_equal(got["logp"], logp[order])
+    assert np.array_equal(got["summary"], summ[order].astype(np.float64))
+    budget = 1000 * 80                                     # 80 bytes per call: id, logp, 8 summary values
+    for name in ("s1", "s2"):
+        write_outputs(str(tmp_path / name), ids, logp, summ, max_bytes=budget)
+    s1, s2 = ({k: np.load(str(tmp_path / name / (k + ".npy"))) for k in shapes} for name in ("s1", "s2"))
+    assert sum(a.nbytes for a in s1.values()) <= budget and len(s1["call_id"]) == 1000
+    assert all(np.array_equal(s1[k], s2[k]) for k in shapes)
+    picked = s1["call_id"].astype(np.int64)
+    assert np.all(np.diff(picked) > 0) and np.array_equal(s1["logp"], got["logp"][picked])
+    assert np.array_equal(s1["summary"], got["summary"][picked])
 
 
 def test_committed_bench_line_keeps_the_contract():

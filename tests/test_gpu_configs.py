@@ -182,6 +182,25 @@ def test_c3_two_ranks_gather_equals_one_rank(tmp_path):
     assert d1["efficiency_measured"] == 1.0 and d1["same_workload_n1"]["where"] == "this line"
 
 
+def test_dump_outputs_is_the_timed_path_on_the_seeded_inputs(tmp_path):
+    """bench.py --dump-outputs DIR (C1, 3000 reads here): float64 .npy files of every call's logp and summary from the last
+    timed step, the same on a second run with the same arguments, and equal to one-shot scoring of the same seeded reads."""
+    from advntr_amd import _lib, workloads
+    common = ["--reads", "3000", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-s300"]
+    dumps = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dumps:
+        line = _bench(common + ["--dump-outputs", d])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["config"]["calls_this_rank"] == 3000
+    got = [{k: np.load(os.path.join(d, k + ".npy")) for k in ("call_id", "logp", "summary")} for d in dumps]
+    for k in ("call_id", "logp", "summary"):
+        assert got[0][k].dtype == np.float64 and np.array_equal(got[0][k], got[1][k]), k
+    assert np.array_equal(got[0]["call_id"], np.arange(3000)) and got[0]["summary"].shape == (3000, _lib.SUMMARY_INTS)
+    locus = workloads.ref150()
+    reads = workloads.make_reads(np.random.default_rng(20240601), locus, 3000, 150)
+    logp, summ, _ = locus.model.viterbi_batch(reads)
+    assert np.array_equal(got[0]["logp"], logp) and np.array_equal(got[0]["summary"], summ.astype(np.float64))
+
+
 def test_emulated_rank_processes_run_the_n_rank_line():
     """--emulate-ranks 2 --processes: two rank PROCESSES share this box's GPU through the host communicator and run the 2-rank line
     itself -- what one GPU can show of the host side of an N-rank job: every rank sleeps in its device waits, takes its share of the
