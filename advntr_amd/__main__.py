@@ -1,7 +1,7 @@
 """Thin command line over the engine: `python -m advntr_amd genotype --loci loci.json --reads reads.fa`.
 
-Not a re-implementation of the reference's CLI (/root/reference/advntr/__main__.py, advntr_commands.py: BAM/CRAM
-input is out of scope).  It strings the GPU stages together
+Not a re-implementation of the reference's CLI (/root/reference/advntr/__main__.py, advntr_commands.py: CRAM input is
+out of scope; --alignment takes BAM or SAM text).  It strings the GPU stages together
 for reads that are already extracted: keyword prefilter -> per-locus Viterbi scoring of both strands -> recruit ->
 Illumina aggregation (or PacBio dominant copy numbers) -> the reference's text output (genome_analyzer.py:158-170:
 the VNTR id on one line, the genotype `a/b` on the next).
@@ -89,10 +89,19 @@ def genotype(args):
         return 0
     names, seqs = _read_fasta(args.reads) if args.reads else ([], [])
     samfile = None
-    if args.alignment:     # SAM text (`samtools view -h`): mapped reads are selected per locus, unmapped ones join --reads
-        from . import sam_utils
-        with open(args.alignment) as fh:
-            samfile = sam_utils.parse_sam(fh.read())
+    if args.alignment:     # mapped reads are selected per locus, unmapped ones join --reads
+        from . import bam
+        kind = bam.sniff(args.alignment)
+        if kind == "bgzf":     # BAM: one pass on the GPU keeps the records of the loci's windows and the unmapped ones
+            references = bam.read_header(args.alignment)[0]
+            samfile = bam.open_alignment(args.alignment, bam.vntr_windows(references, [loc["vntr"] for loc in loci]))
+        elif kind == "text":   # SAM text (`samtools view -h`)
+            from . import sam_utils
+            with open(args.alignment) as fh:
+                samfile = sam_utils.parse_sam(fh.read())
+        else:
+            raise SystemExit("%s: %s input is not supported (--alignment takes BAM or SAM text)" %
+                             (args.alignment, "CRAM" if kind == "cram" else "gzip that is not BGZF"))
         seqs = seqs + [r.seq for r in samfile.reads if r.is_unmapped]
     settings.MAX_ERROR_RATE = 0.3 if args.pacbio else 0.05                      # advntr_commands.py:66-71
     if args.pacbio:
@@ -189,8 +198,8 @@ def main(argv=None):
     g.add_argument("--align-repeats", action="store_true",
                    help="align repeat segments of unequal length with the built-in aligner (instead of refusing them)")
     g.add_argument("--reads", help="FASTA / FASTQ of extracted reads")
-    g.add_argument("--alignment", help="SAM text of the sample (e.g. `samtools view -h sample.bam`): mapped reads over each "
-                                       "VNTR are selected as vntr_finder.py:701-750 does, unmapped records are added to --reads")
+    g.add_argument("--alignment", help="BAM file (read on the GPU) or SAM text of the sample: mapped reads over each VNTR are "
+                                       "selected as vntr_finder.py:701-750 does, unmapped records are added to --reads")
     g.add_argument("--pacbio", action="store_true", help="reads are trimmed spanning long reads (error rate 0.3)")
     g.add_argument("--extract-spanning", action="store_true",
                    help="with --pacbio: the reads are whole long reads; find the ones that span each VNTR by aligning its "

@@ -11,7 +11,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ADVNTR_HIP_LIB") or os.path.join(_HERE, "libadvntr_hip.so")   # override: kernel experiments
 
-OK, ERR_ARG, ERR_SYMBOL, ERR_DEVICE, ERR_TOO_LARGE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
+OK, ERR_ARG, ERR_SYMBOL, ERR_DEVICE, ERR_TOO_LARGE, ERR_UNSUPPORTED, ERR_DATA = 0, -1, -2, -3, -4, -5, -6
+BAM_RECORD_OFFSETS, BAM_FIELDS, BAM_STATS = 1, 10, 16
 FLAG_PATH, FLAG_FORCE_GENERIC, FLAG_NO_SUMMARY, FLAG_STREAM, FLAG_ANTIDIAGONAL, FLAG_BOTH_STRANDS = 1, 2, 4, 8, 16, 32
 FLAG_DEEP_TILES = 64
 FLAG_SECOND_QUEUE = 128      # a stream class of its own: see include/advntr_hip.h (two copies of a batch whose passes overlap)
@@ -85,6 +86,16 @@ SYMBOLS = {
     "advntr_comm_gather_results_finish": (ctypes.c_int, [_vp, _vp, _vp]),
     "advntr_comm_last_gather_ms": (ctypes.c_int, [_vp, _vp]),
     "advntr_comm_gather_bytes": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "advntr_bgzf_scan": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "advntr_bam_header": (ctypes.c_int, [ctypes.c_char_p, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "advntr_bgzf_inflate": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp]),
+    "advntr_bam_walk_host": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "advntr_bam_decode_host": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "advntr_bam_select": (_vp, [ctypes.c_char_p, _i32, _vp, _vp, _vp, _i64, _u32]),
+    "advntr_bam_kept_info": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "advntr_bam_kept_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "advntr_bam_kept_offsets": (ctypes.c_int, [_vp, _vp]),
+    "advntr_bam_kept_destroy": (None, [_vp]),
 }
 
 _lib = None

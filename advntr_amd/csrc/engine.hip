@@ -1496,3 +1496,4 @@ extern "C" int advntr_host_threads(void) { return host_cpu_limit(); }
 #include "abi_recruit.h"
 #include "abi_comm.h"
 #include "abi_genotype.h"
+#include "abi_bam.h"

@@ -30,6 +30,8 @@ extern "C" {
 #define ADVNTR_ERR_DEVICE      -3   /* HIP runtime error; text in advntr_last_error()                    */
 #define ADVNTR_ERR_TOO_LARGE   -4   /* model does not fit the on-chip trellis rows       */
 #define ADVNTR_ERR_UNSUPPORTED -5
+#define ADVNTR_ERR_DATA        -6   /* malformed or corrupt input file (BGZF framing, DEFLATE stream, CRC32, BAM record);
+                                       advntr_last_error() names the file offset                                          */
 
 /* flags for advntr_viterbi_batch / advntr_batch_run */
 #define ADVNTR_FLAG_PATH          1u  /* also return the Viterbi paths (state indices, start..end)      */
@@ -345,6 +347,57 @@ int advntr_comm_last_gather_ms(const advntr_comm *comm, float *ms);
 /* ragged gather of host byte strings through the devices (the genotype driver's per-locus result rows):
  * counts[r] = bytes of rank r; dst (root only) receives them rank after rank.                                   */
 int advntr_comm_gather_bytes(advntr_comm *comm, int32_t root, const void *src, const int64_t *counts, void *dst);
+
+/* ---- BAM input (replaces pysam.AlignmentFile: fetch per VNTR, vntr_finder.py:701-750, and the whole-file
+ * `samtools view -b -f4` + bam2fq of the unmapped reads, sam_utils.py:9-23) ----------------------------------------
+ * BGZF framing and the BAM header are read on the host (no GPU needed); inflating and the record selection run on the
+ * device and fail with ADVNTR_ERR_DEVICE without one.  Offsets are 64-bit throughout.  Malformed input is ADVNTR_ERR_DATA
+ * with the file offset of the first bad block or record in advntr_last_error().                                     */
+typedef struct advntr_bam_kept advntr_bam_kept;
+/* framing of a BGZF file held in memory (htslib's bgzf_read_block header checks): block b starts at block_off[b] and has
+ * block_bytes[b] compressed bytes (BSIZE + 1) and isize[b] uncompressed ones.  Arrays are filled up to `capacity`;
+ * *n_blocks is the full count.  A truncated block, a gzip member without the BC extra field, or an ISIZE above 65536
+ * is ADVNTR_ERR_DATA.                                                                                                */
+int advntr_bgzf_scan(const uint8_t *data, int64_t n_bytes, int64_t *block_off, int32_t *block_bytes, uint32_t *isize,
+                     int64_t capacity, int64_t *n_blocks);
+/* the binary header of a BAM file (SAMv1 4.2: l_text, text, n_ref, {l_name, name, l_ref}): reference names NUL-separated
+ * into names (names_capacity bytes), lengths into lengths (refs_capacity); *n_ref, *names_bytes and *header_bytes (the
+ * uncompressed offset of the first record) are always set, so a first call with zero capacities sizes the second.
+ * Replaces AlignmentFile.references / .lengths.                                                                      */
+int advntr_bam_header(const char *path, char *names, int64_t names_capacity, int32_t *lengths, int32_t refs_capacity,
+                      int32_t *n_ref, int64_t *names_bytes, int64_t *header_bytes);
+/* inflate a whole BGZF file held in memory on the device, ISIZE and CRC32 checked per block: out[out_capacity] receives
+ * the concatenated blocks, *out_len their length (sized by advntr_bgzf_scan's isize sum).                             */
+int advntr_bgzf_inflate(const uint8_t *data, int64_t n_bytes, uint8_t *out, int64_t out_capacity, int64_t *out_len);
+/* the sequential record-chain walk over inflated bytes buf[n_bytes] from `start`: offsets of the complete records into
+ * offsets (capacity), *n_records, *end = start of the first incomplete record (n_bytes when none).                    */
+int advntr_bam_walk_host(const uint8_t *buf, int64_t n_bytes, int64_t start, int64_t *offsets, int64_t capacity,
+                         int64_t *n_records, int64_t *end);
+/* decode records of buf at offsets[n_records] as advntr_bam_kept_fetch does: fields[ADVNTR_BAM_FIELDS] per record and
+ * text (text_capacity bytes; text_off[n_records + 1] always filled, so text_off[n_records] sizes a second call).       */
+int advntr_bam_decode_host(const uint8_t *buf, int64_t n_bytes, const int64_t *offsets, int64_t n_records, int32_t *fields,
+                           uint8_t *text, int64_t text_capacity, int64_t *text_off);
+/* One streaming pass over a BAM file on the device: chunks of chunk_bytes compressed bytes (0 = 256 MiB) are uploaded
+ * while the previous chunk is processed, inflated, split into records (exact: the per-block chain walks are confirmed
+ * against each other, a failing stretch is walked sequentially on the host), and the records pysam would have yielded are
+ * kept in file order: the first 5 of the file (samfile.head(5)), every mapped record overlapping one of the windows
+ * (SamFile.fetch: half-open, reference_start + 1 as the end without CIGAR; windows of reference r are
+ * [win_start[k], win_end[k]) for k in win_ptr[r] .. win_ptr[r+1]), and every unmapped (0x4) record.  Only those are
+ * decoded.  flags: ADVNTR_BAM_RECORD_OFFSETS also keeps the uncompressed offset of every record.  NULL on error.    */
+#define ADVNTR_BAM_RECORD_OFFSETS 1u
+#define ADVNTR_BAM_FIELDS 10      /* refID, pos, flag, mapq, reference_end (-1 = None), name, seq, qual, cigar text lengths, 0 */
+#define ADVNTR_BAM_STATS 16       /* see advntr_bam_kept_info                                                             */
+advntr_bam_kept *advntr_bam_select(const char *path, int32_t n_ref, const int32_t *win_ptr, const int64_t *win_start,
+                                   const int64_t *win_end, int64_t chunk_bytes, uint32_t flags);
+/* stats[ADVNTR_BAM_STATS]: blocks, compressed bytes, uncompressed bytes, records, kept, chunks, file-read ms, framing ms,
+ * upload ms (copy stream), inflate kernel ms, boundary ms (device walks, checks, fallback, offsets), fallback blocks,
+ * fallback ms, selection ms (select + decode kernels and downloads), total ms, 0                                     */
+int advntr_bam_kept_info(const advntr_bam_kept *kept, int64_t *n_kept, int64_t *text_bytes, int64_t *n_offsets, double *stats);
+/* kept records in file order: fields[n_kept][ADVNTR_BAM_FIELDS], text (record k is text[text_off[k] .. text_off[k+1]):
+ * name | sequence ('*' if none) | qualities (raw Phred, absent when the first byte is 0xFF) | CIGAR ('*' if none)) */
+int advntr_bam_kept_fetch(const advntr_bam_kept *kept, int32_t *fields, uint8_t *text, int64_t *text_off);
+int advntr_bam_kept_offsets(const advntr_bam_kept *kept, int64_t *offsets);
+void advntr_bam_kept_destroy(advntr_bam_kept *kept);
 
 #ifdef __cplusplus
 }
