@@ -89,6 +89,10 @@ def genotype(args):
         return 0
     names, seqs = _read_fasta(args.reads) if args.reads else ([], [])
     samfile = None
+    if args.alignment and args.pacbio:
+        settings.MAX_ERROR_RATE = 0.3                                           # advntr_commands.py:66-71
+        return finish(sharding.run_sharded([len(loc["pattern"]) for loc in loci],
+                                           _pacbio_alignment_job(args, loci, seqs, row), comm))
     if args.alignment:     # mapped reads are selected per locus, unmapped ones join --reads
         from . import bam
         kind = bam.sniff(args.alignment)
@@ -178,6 +182,48 @@ def genotype(args):
     return finish(sharding.run_sharded(work, genotype_job, comm))
 
 
+def _pacbio_alignment_job(args, loci, seqs, row):
+    """find_repeat_counts_from_pacbio_alignment_file (genome_analyzer.py:210-233, vntr_finder.py:640-651): per locus, the mapped
+    records that span it, trimmed by their CIGAR (on the device for BAM, vntr_finder's mirror for SAM text), joined by the
+    unmapped records (+ --reads) that pass the long-read keyword filter and span it by flank alignment; one genotype step for
+    all loci of a rank.  Returns the sharded job."""
+    from . import bam, filtering, vntr_finder
+    vntrs = [loc["vntr"] for loc in loci]
+    kind = bam.sniff(args.alignment)
+    if kind == "bgzf":
+        references = bam.read_header(args.alignment)[0]
+        windows = [w + (i,) for i, w in enumerate(bam.vntr_windows(references, vntrs))]
+        spans = bam.open_alignment_spans(args.alignment, windows)
+        mapped = [[t[1] for t in ts] for ts in spans.spanning(len(loci))]
+        unmapped = [r.seq for r in spans.unmapped]
+    elif kind == "text":
+        from . import sam_utils
+        with open(args.alignment) as fh:
+            samfile = sam_utils.parse_sam(fh.read())
+        mapped = [[t[1] for t in vntr_finder.get_spanning_reads_of_aligned_pacbio_reads(v, samfile)] for v in vntrs]
+        unmapped = [r.seq for r in samfile.reads if r.is_unmapped]
+    else:
+        raise SystemExit("%s: %s input is not supported (--alignment takes BAM or SAM text)" %
+                         (args.alignment, "CRAM" if kind == "cram" else "gzip that is not BGZF"))
+    seqs = seqs + unmapped
+    # adVNTR-Filtering with the long-read keywords (the flanks' last / first 80 bases, vntr_finder.py:151-152)
+    fasta = "".join(">%d\n%s\n" % (i, s.upper()) for i, s in enumerate(seqs))
+    keywords = {int(loc["id"]): filtering.get_keywords_for_filtering(loc["left"], loc["repeat_segments"], loc["right"],
+                                                                       loc["pattern"], False) for loc in loci}
+    _, ids = filtering.get_filtered_read_ids(fasta, keywords, min_matches=args.min_matches)
+    cands = [[seqs[i] for i in sorted(int(n) for n in ids.get(int(loc["id"]), ()))] for loc in loci]
+
+    def job(indices):
+        unaligned = vntr_finder.extract_spanning_reads_multi([(loci[i]["left"], loci[i]["right"]) for i in indices],
+                                                            [cands[i] for i in indices])
+        desc = [(loci[i]["left"], loci[i]["right"], loci[i]["repeat_segments"], loci[i]["pattern"]) for i in indices]
+        spanning = [mapped[i] + [t[0] for t in u[0]] for i, u in zip(indices, unaligned)]
+        res = vntr_finder.genotype_pacbio_loci(desc, spanning, accuracy_filter=args.accuracy_filter, is_haploid=args.haploid,
+                                               chunks=max(1, min(8, len(desc) // 4)), trimmed=True)
+        return [row(loci[i], r) for i, r in zip(indices, res)]
+    return job
+
+
 def _frameshift_row(loc, cand, read_length, hmm_utils, vntr_finder):
     copies = vntr_finder.get_copies_for_hmm(read_length, len(loc["pattern"]))
     model = hmm_utils.get_read_matcher_model(loc["left"][-read_length:], loc["right"][:read_length],
@@ -200,7 +246,9 @@ def main(argv=None):
     g.add_argument("--reads", help="FASTA / FASTQ of extracted reads")
     g.add_argument("--alignment", help="BAM file (read on the GPU) or SAM text of the sample: mapped reads over each VNTR are "
                                        "selected as vntr_finder.py:701-750 does, unmapped records are added to --reads")
-    g.add_argument("--pacbio", action="store_true", help="reads are trimmed spanning long reads (error rate 0.3)")
+    g.add_argument("--pacbio", action="store_true", help="reads are trimmed spanning long reads (error rate 0.3); with "
+                   "--alignment: the mapped long reads that span each VNTR are trimmed by their CIGAR, the unmapped ones "
+                   "(and --reads) are filtered and trimmed by flank alignment (vntr_finder.py:640-651)")
     g.add_argument("--extract-spanning", action="store_true",
                    help="with --pacbio: the reads are whole long reads; find the ones that span each VNTR by aligning its "
                         "flanks (vntr_finder.py:324-371; GPU Smith-Waterman, parity with biopython unpinned) and trim them")
@@ -218,8 +266,8 @@ def main(argv=None):
     if args.cmd == "genotype":
         if not args.reads and not args.alignment:
             ap.error("genotype needs --reads and/or --alignment")
-        if args.alignment and (args.pacbio or args.frameshift):
-            ap.error("--alignment is the Illumina copy-number path")
+        if args.alignment and args.frameshift:
+            ap.error("--alignment does not go with --frameshift")
         args.comm = None
         try:
             return genotype(args)

@@ -208,3 +208,116 @@ def open_alignment(path, windows, chunk_bytes=0, record_offsets=False):
     keys = ("blocks", "compressed_bytes", "uncompressed_bytes", "records", "kept", "chunks", "read_ms", "framing_ms",
             "upload_ms", "inflate_kernel_ms", "boundary_ms", "fallback_blocks", "fallback_ms", "select_ms", "total_ms")
     return BamFile(references, reads, windows, dict(zip(keys, (float(x) for x in stats))), offsets)
+
+
+# ------------------------------------------------------------------------------------------------
+# Long reads (vntr_finder.py:373-471, 640-651): the mapped records that span each window, trimmed to its flanks on the device
+# ------------------------------------------------------------------------------------------------
+SPAN_OK, SPAN_UNMAPPED, SPAN_NO_ALIGNED, SPAN_NOT_SPANNING, SPAN_SHORT_FLANK, SPAN_NO_SEQ = range(6)
+SPAN_FLANK, SPAN_MIN_FLANK = 100, 10        # hmm_flanking_region_size, min_flanking_bp (vntr_finder.py:374-375)
+_SPAN_STATS = ("pairs", "spanning", "rejected_unmapped", "rejected_no_aligned", "rejected_not_spanning", "rejected_short_flank",
+               "rejected_no_seq", "span_kernel_ms", "trimmed_bytes", "unmapped_bytes", "whole_bytes", "trim_kernel_ms")
+_BAM_STATS = ("blocks", "compressed_bytes", "uncompressed_bytes", "records", "kept", "chunks", "read_ms", "framing_ms",
+              "upload_ms", "inflate_kernel_ms", "boundary_ms", "fallback_blocks", "fallback_ms", "select_ms", "total_ms")
+
+
+def _pieces(pairs, text, text_off):
+    """per pair (window, locus, record, status, rs, end, left, tr, right, name length) -> (name, piece) of the spanning ones"""
+    tb = bytes(text)
+    out = []
+    for k in range(len(pairs)):
+        if pairs[k, 3] != SPAN_OK:
+            out.append(None)
+            continue
+        a, nl = int(text_off[k]), int(pairs[k, 9])
+        out.append((tb[a:a + nl].decode(), tb[a + nl:int(text_off[k + 1])].decode()))
+    return out
+
+
+def span_host(raw, offsets, windows, flank=SPAN_FLANK, min_flank=SPAN_MIN_FLANK):
+    """The long-read rule on the host (the device's code): pair k = the record of uncompressed bytes `raw` at offsets[k] and the
+    window windows[k] = (vs, ve).  Returns (pairs [n, BAM_SPAN_FIELDS] int64, [(name, piece) or None per pair])."""
+    L = _lib.load()
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(offs)
+    ws = np.array([int(w[0]) for w in windows] or [0], np.int64)
+    we = np.array([int(w[1]) for w in windows] or [0], np.int64)
+    toff = np.zeros(n + 1, np.int64)
+    pairs = np.zeros((max(1, n), _lib.BAM_SPAN_FIELDS), np.int64)
+    _lib.check(L.advntr_bam_span_host(_lib.ptr(buf), len(buf), _lib.ptr(offs), _lib.ptr(ws), _lib.ptr(we), n, flank, min_flank,
+                                      None, None, 0, _lib.ptr(toff)))
+    text = np.zeros(max(1, int(toff[n])), np.uint8)
+    _lib.check(L.advntr_bam_span_host(_lib.ptr(buf), len(buf), _lib.ptr(offs), _lib.ptr(ws), _lib.ptr(we), n, flank, min_flank,
+                                      _lib.ptr(pairs), _lib.ptr(text), len(text), _lib.ptr(toff)))
+    return pairs[:n], _pieces(pairs[:n], text, toff)
+
+
+class BamSpans(object):
+    """One long-read pass: `pairs` (every (window, mapped record) pair, by window then file order, BAM_SPAN_FIELDS int64 each),
+    `pieces[k]` = (query name, trimmed sequence) of pair k when it spans, else None; `unmapped` = the unmapped records as
+    SamRead objects (file order); `stats`."""
+
+    def __init__(self, references, pairs, pieces, unmapped, stats):
+        self.references, self.pairs, self.pieces, self.unmapped, self.stats = references, pairs, pieces, unmapped, stats
+
+    def spanning(self, n_windows):
+        """per window (input order): [(query_name, trimmed sequence, left_bp, tr_bp, right_bp)] of its spanning records"""
+        out = [[] for _ in range(n_windows)]
+        for k, piece in enumerate(self.pieces):
+            if piece is not None:
+                p = self.pairs[k]
+                out[int(p[0])].append((piece[0], piece[1], int(p[6]), int(p[7]), int(p[8])))
+        return out
+
+
+def open_alignment_spans(path, windows, chunk_bytes=0, flank=SPAN_FLANK, min_flank=SPAN_MIN_FLANK):
+    """One pass over the aligned long-read BAM at `path` on the device.  windows: (reference name, vs, ve[, locus id]) as
+    vntr_windows gives them; windows on references the file does not have get no pairs.  Returns a BamSpans; its
+    spanning(len(windows)) lists the trimmed mapped reads of every window."""
+    L = _lib.load()
+    references, _, _ = read_header(path)
+    index = {name: i for i, name in enumerate(references)}
+    per_ref = [[] for _ in references]
+    for k, w in enumerate(windows):
+        if w[0] in index:
+            per_ref[index[w[0]]].append((int(w[1]), int(w[2]), k, int(w[3]) if len(w) > 3 else k))
+    win_ptr = np.zeros(len(references) + 1, np.int32)
+    np.cumsum([len(w) for w in per_ref], out=win_ptr[1:])
+    flat = [w for ws in per_ref for w in ws]
+    ws = np.array([w[0] for w in flat] or [0], np.int64)
+    we = np.array([w[1] for w in flat] or [0], np.int64)
+    locus = np.array([w[3] for w in flat] or [0], np.int64)
+    h = L.advntr_bam_select_spans(path.encode(), len(references), _lib.ptr(win_ptr), _lib.ptr(ws), _lib.ptr(we), _lib.ptr(locus),
+                                  int(flank), int(min_flank), int(chunk_bytes), 0)
+    if not h:
+        err = _lib.last_error()
+        raise _lib.EngineError(_lib.ERR_DEVICE if "no HIP device" in err else _lib.ERR_DATA, err)
+    try:
+        n_pairs, text_bytes, n_unmapped, ubytes = (ctypes.c_int64() for _ in range(4))
+        stats = np.zeros(_lib.BAM_SPAN_STATS, np.float64)
+        _lib.check(L.advntr_bam_spans_info(h, ctypes.byref(n_pairs), ctypes.byref(text_bytes), ctypes.byref(n_unmapped),
+                                           ctypes.byref(ubytes), _lib.ptr(stats)))
+        pairs = np.zeros((max(1, n_pairs.value), _lib.BAM_SPAN_FIELDS), np.int64)
+        text = np.zeros(max(1, text_bytes.value), np.uint8)
+        toff = np.zeros(n_pairs.value + 1, np.int64)
+        fields = np.zeros(max(1, n_unmapped.value) * _lib.BAM_FIELDS, np.int32)
+        utext = np.zeros(max(1, ubytes.value), np.uint8)
+        utoff = np.zeros(n_unmapped.value + 1, np.int64)
+        _lib.check(L.advntr_bam_spans_fetch(h, _lib.ptr(pairs), _lib.ptr(text), _lib.ptr(toff), _lib.ptr(fields), _lib.ptr(utext),
+                                            _lib.ptr(utoff)))
+    finally:
+        L.advntr_bam_spans_destroy(h)
+    pairs = pairs[:n_pairs.value]
+    # the device reports windows by their index in its (per-reference) list: back to the caller's index
+    if len(pairs):
+        pairs[:, 0] = np.array([w[2] for w in flat], np.int64)[pairs[:, 0]]
+        order = np.argsort(pairs[:, 0], kind="stable")
+    else:
+        order = np.zeros(0, np.int64)
+    pieces = _pieces(pairs, text, toff)
+    pairs, pieces = pairs[order], [pieces[i] for i in order.tolist()]
+    unmapped = _reads(references, fields[:n_unmapped.value * _lib.BAM_FIELDS], utext, utoff)
+    st = dict(zip(_BAM_STATS, (float(x) for x in stats[:15])))
+    st.update(zip(_SPAN_STATS, (float(x) for x in stats[16:])))
+    return BamSpans(references, pairs, pieces, unmapped, st)

@@ -337,7 +337,7 @@ def genotype_loci_pipelined(loci, read_lists, scaled_scores=None, accuracy_filte
 
 
 def genotype_pacbio_loci(loci, read_lists, accuracy_filter=False, is_haploid=False, chunks=16, threads=0, timings=None,
-                         flanking_region_size=100):
+                         flanking_region_size=100, trimmed=False):
     """VNTRFinder.find_repeat_count_from_pacbio_reads (vntr_finder.py:652-665) for many loci at once, from the WHOLE long
     reads to the RU-count genotypes: loci = [(left_flanking_region, right_flanking_region, repeat_segments, pattern), ...],
     read_lists[i] = the candidate reads of locus i (what the keyword filter hands over).  Per piece of the locus set:
@@ -349,7 +349,10 @@ def genotype_pacbio_loci(loci, read_lists, accuracy_filter=False, is_haploid=Fal
     call (:568-580) run once at the end on host threads (advntr_genotype_observed).  settings.MAX_ERROR_RATE is the
     caller's (0.3 for PacBio, advntr_commands.py).  Returns one GenotypeResult per locus, as the reference builds it
     (:665): GenotypeResult(copy_numbers, n_spanning, n_spanning, 0, max_prob).  timings (a dict) receives wall seconds per
-    stage.  Extraction is PARITY UNPINNED with respect to biopython (see extract_spanning_reads)."""
+    stage.  Extraction is PARITY UNPINNED with respect to biopython (see extract_spanning_reads).  With trimmed=True,
+    read_lists[i] are already the spanning reads of locus i, trimmed to its flanks (the mapped reads of an aligned file and
+    the extracted unaligned ones, find_repeat_count_from_pacbio_alignment_file, :640-651): extraction is skipped and the
+    models, the scoring batch and the call are the same."""
     import queue
     import threading
     import time
@@ -369,9 +372,18 @@ def genotype_pacbio_loci(loci, read_lists, accuracy_filter=False, is_haploid=Fal
 
     def encode_whole(k):
         lo, hi = cuts[k], cuts[k + 1]
+        if trimmed:         # the pieces as they are, grouped by locus: what extract() hands on
+            pieces = [s for rl in read_lists[lo:hi] for s in rl]
+            if not pieces:
+                return None
+            codes, off, _ = _lib.encode_ascii(pieces, threads)
+            piece_locus = np.repeat(np.arange(hi - lo, dtype=np.int32), [len(rl) for rl in read_lists[lo:hi]])
+            return codes, off, piece_locus
         return _vf._spanning_prepare([(l[0], l[1]) for l in loci[lo:hi]], read_lists[lo:hi], flanking_region_size)
 
     def extract(k, prep):
+        if trimmed:
+            return prep
         # (locus, read) uses that span -> the trimmed pieces as encoded reads, grouped by locus (hits come ordered by use)
         H = _vf._spanning_align(prep)
         if H is None or len(H["use"]) == 0:

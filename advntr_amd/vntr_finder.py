@@ -537,6 +537,72 @@ def extract_spanning_reads_multi(flank_pairs, read_lists, flanking_region_size=1
 
 
 # ------------------------------------------------------------------------------------------------
+# Mapped long reads of an alignment file (vntr_finder.py:373-420, 442-471): the CIGAR says where the flanks are, no alignment
+# ------------------------------------------------------------------------------------------------
+SPAN_OK, SPAN_UNMAPPED, SPAN_NO_ALIGNED, SPAN_NOT_SPANNING, SPAN_SHORT_FLANK, SPAN_NO_SEQ = range(6)
+
+
+def pacbio_mapped_read_span(read, vntr_start, vntr_end, flanking_region_size=100, min_flanking_bp=10):
+    """check_if_pacbio_mapped_read_spans_vntr on a SamRead (CIGAR text), the host mirror of the device rule (csrc/bam_spans.h):
+    (status, piece or None, left_bp, tr_bp, right_bp).  Aligned bases are those of M = X; query indices count S and I too.
+    A CIGAR that is the <l_seq>S<ref_len>N placeholder of a CG tag raises ValueError."""
+    from .sam_utils import _CIGAR
+    if read.is_unmapped:
+        return SPAN_UNMAPPED, None, 0, 0, 0
+    ops = [] if read.cigar in ("*", None) else [(int(n), op) for n, op in _CIGAR.findall(read.cigar)]
+    seq = "" if read.seq in ("*", None) else read.seq
+    if len(ops) == 2 and ops[0][1] == "S" and ops[0][0] == len(seq) > 0 and ops[1][1] == "N":
+        raise ValueError("read %s: its CIGAR is kept in the CG tag (<l_seq>S<ref_len>N placeholder), which is not decoded"
+                         % read.query_name)
+    region_start, region_end = vntr_start - flanking_region_size, vntr_end + flanking_region_size
+    first = last = rs = re_ = None
+    left = tr = right = 0
+    q, ref = 0, read.reference_start
+    for n, op in ops:
+        if op in "M=X" and n > 0:
+            first = ref if first is None else first
+            last = ref + n - 1
+            a, b = max(ref, region_start), min(ref + n, vntr_start)                # left flank, in closed form
+            if b > a:
+                rs = q + (a - ref) if rs is None else rs
+                left += b - a
+            tr += max(0, min(ref + n, vntr_end) - max(ref, vntr_start))
+            a, b = max(ref, vntr_end), min(ref + n, region_end)
+            if b > a:
+                re_ = q + (a - ref) if re_ is None else re_
+                right += b - a
+        if op in "MIS=X":
+            q += n
+        if op in "MDN=X":
+            ref += n
+    if first is None:
+        return SPAN_NO_ALIGNED, None, left, tr, right
+    if not (first <= vntr_start - min_flanking_bp and vntr_end + min_flanking_bp < last):
+        return SPAN_NOT_SPANNING, None, left, tr, right
+    if left < min_flanking_bp or right < min_flanking_bp:
+        return SPAN_SHORT_FLANK, None, left, tr, right
+    if not seq:
+        return SPAN_NO_SEQ, None, left, tr, right
+    return SPAN_OK, seq[rs:re_ + right], left, tr, right
+
+
+def get_spanning_reads_of_aligned_pacbio_reads(reference_vntr, samfile):
+    """get_spanning_reads_of_aligned_pacbio_reads (vntr_finder.py:442-471) over a SamFile: the mapped records fetched over the
+    VNTR, in file order, that span it: [(query_name, trimmed sequence, left_bp, tr_bp, right_bp)]."""
+    from .sam_utils import get_reference_genome_of_alignment_file
+    vntr_start = reference_vntr.start_point
+    vntr_end = vntr_start + reference_vntr.get_length()
+    reference = get_reference_genome_of_alignment_file(samfile)
+    chromosome = reference_vntr.chromosome if reference == 'HG19' else reference_vntr.chromosome[3:]
+    out = []
+    for read in samfile.fetch(chromosome, vntr_start, vntr_end):
+        status, piece, left, tr, right = pacbio_mapped_read_span(read, vntr_start, vntr_end)
+        if status == SPAN_OK:
+            out.append((read.query_name, piece, left, tr, right))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # Read selection from an alignment file (vntr_finder.py:701-767): mapped reads over the locus + filtered unmapped reads
 # ------------------------------------------------------------------------------------------------
 class SelectedRead(object):

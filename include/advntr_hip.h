@@ -399,6 +399,47 @@ int advntr_bam_kept_fetch(const advntr_bam_kept *kept, int32_t *fields, uint8_t 
 int advntr_bam_kept_offsets(const advntr_bam_kept *kept, int64_t *offsets);
 void advntr_bam_kept_destroy(advntr_bam_kept *kept);
 
+/* ---- Long reads of an aligned BAM (VNTRFinder.find_repeat_count_from_pacbio_alignment_file, vntr_finder.py:640-651) --
+ * For a mapped record and a VNTR window [vs, ve) (flank F, minimum flank MIN; the reference's 100 and 10): aligned bases are
+ * those of M = X ops (query indices count S and I too).  The record spans when its first aligned reference position is
+ * <= vs - MIN and its last > ve + MIN; left / tr / right = aligned bases in [vs-F, vs), [vs, ve), [ve, ve+F); rs / re =
+ * query index of the first aligned base of the left / right range; left or right below MIN rejects it; the piece is
+ * SEQ[rs : re + right] clamped to l_seq (vntr_finder.py:373-420).  Status per pair: */
+#define ADVNTR_SPAN_OK            0   /* spanning: text holds name | SEQ[rs, end)                                        */
+#define ADVNTR_SPAN_UNMAPPED      1   /* flag 0x4                                                                        */
+#define ADVNTR_SPAN_NO_ALIGNED    2   /* no aligned base                                                                 */
+#define ADVNTR_SPAN_NOT_SPANNING  3   /* first / last aligned position fails the spanning test                           */
+#define ADVNTR_SPAN_SHORT_FLANK   4   /* left or right below MIN                                                         */
+#define ADVNTR_SPAN_NO_SEQ        5   /* l_seq == 0                                                                      */
+/* A record whose CIGAR is the <l_seq>S<ref_len>N placeholder of a CG:B,I tag is ADVNTR_ERR_DATA naming the record.    */
+#define ADVNTR_BAM_SPAN_FIELDS 10  /* per pair (int64): window, locus, record index, status, rs, end, left, tr, right, name length */
+#define ADVNTR_BAM_SPAN_STATS 28   /* see advntr_bam_spans_info                                                          */
+typedef struct advntr_bam_spans advntr_bam_spans;
+/* the rule on the host over uncompressed bytes: pair k = the record at offsets[k] and the window [win_start[k], win_end[k]);
+ * pairs[n][ADVNTR_BAM_SPAN_FIELDS] (window = record = k, locus = -1), text of the spanning pairs into text (text_capacity);
+ * text_off[n + 1] is always filled, so text_off[n] sizes a second call.                                               */
+int advntr_bam_span_host(const uint8_t *buf, int64_t n_bytes, const int64_t *offsets, const int64_t *win_start,
+                         const int64_t *win_end, int64_t n, int32_t flank, int32_t min_flank, int64_t *pairs, uint8_t *text,
+                         int64_t text_capacity, int64_t *text_off);
+/* the streaming pass of advntr_bam_select for long reads: windows as there, win_locus[k] = the locus id of window k.  Every
+ * mapped record overlapping a window gives one pair per window it overlaps (ordered by window, then file order), and the
+ * rule runs on the device (one wavefront per pair); only the name and the piece of a spanning pair are decoded.  Unmapped
+ * (0x4) records are kept and decoded whole as advntr_bam_select keeps them; the file's first records are not.  flags: 0.
+ * NULL on error.                                                                                                       */
+advntr_bam_spans *advntr_bam_select_spans(const char *path, int32_t n_ref, const int32_t *win_ptr, const int64_t *win_start,
+                                          const int64_t *win_end, const int64_t *win_locus, int32_t flank, int32_t min_flank,
+                                          int64_t chunk_bytes, uint32_t flags);
+/* stats[ADVNTR_BAM_SPAN_STATS]: 0-15 as advntr_bam_kept_info (kept = unmapped records), pairs, spanning, rejected as
+ * unmapped, no aligned base, not spanning, short flank, no sequence, span kernel ms, trimmed text bytes, unmapped text
+ * bytes, text bytes the whole decode of the paired records would have made, trim decode kernel ms                      */
+int advntr_bam_spans_info(const advntr_bam_spans *spans, int64_t *n_pairs, int64_t *text_bytes, int64_t *n_unmapped,
+                          int64_t *unmapped_text_bytes, double *stats);
+/* pairs[n_pairs][ADVNTR_BAM_SPAN_FIELDS]; pair k's text is text[text_off[k] .. text_off[k+1]) (empty unless spanning);
+ * the unmapped records as advntr_bam_kept_fetch gives them                                                             */
+int advntr_bam_spans_fetch(const advntr_bam_spans *spans, int64_t *pairs, uint8_t *text, int64_t *text_off, int32_t *fields,
+                           uint8_t *unmapped_text, int64_t *unmapped_text_off);
+void advntr_bam_spans_destroy(advntr_bam_spans *spans);
+
 #ifdef __cplusplus
 }
 #endif
