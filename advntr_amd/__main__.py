@@ -1,4 +1,5 @@
-"""Thin command line over the engine: `python -m advntr_amd genotype --loci loci.json --reads reads.fa`.
+"""Thin command line over the engine: `python -m advntr_amd genotype --loci loci.json --reads reads.fa`, and the model
+database commands `addmodel`, `delmodel` and `viewmodel` (advntr_commands.py:145-223).
 
 Not a re-implementation of the reference's CLI (/root/reference/advntr/__main__.py, advntr_commands.py: CRAM input is
 out of scope; --alignment takes BAM or SAM text).  It strings the GPU stages together
@@ -233,6 +234,97 @@ def _frameshift_row(loc, cand, read_length, hmm_utils, vntr_finder):
     return "%s\n%s\n" % (loc["id"], result)
 
 
+def _print_error(parser, msg):
+    """advntr_commands.py:23-25: the command's help, then the error, exit status 1."""
+    parser.print_help()
+    sys.exit("\nERROR: %s" % msg)
+
+
+def _print_models(reference_vntrs):
+    """print_models, advntr_commands.py:145-153 (its tabs included)."""
+    print('VNTR ID\t| Chr\t| Gene\t| Start Position | Pattern')
+    print('--------------------------------------------------')
+    for ref_vntr in reference_vntrs:
+        gene_name = ref_vntr.gene_name
+        if len(gene_name) < 7:
+            gene_name += '\t'
+        print('%s\t| %s\t|%s| %s\t | %s' % (ref_vntr.id, ref_vntr.chromosome, gene_name, ref_vntr.start_point,
+                                            ref_vntr.pattern))
+
+
+def view_model(args, parser):
+    """view_model, advntr_commands.py:156-176."""
+    from . import models
+    if args.pattern:
+        for element in set(args.pattern.upper()):
+            if element not in {'A', 'C', 'G', 'T'}:
+                _print_error(parser, 'Pattern should only contain A, C, G, T')
+    if args.models is None:
+        _print_error(parser, '--models is required')
+    genes = [gene.upper() for gene in args.gene.split(',') if gene]
+    results = []
+    for ref_vntr in models.load_unique_vntrs_data(args.models):
+        if len(genes) and ref_vntr.gene_name.upper() not in genes:
+            continue
+        if args.pattern and ref_vntr.pattern != args.pattern.upper():
+            continue
+        results.append(ref_vntr)
+    _print_models(results)
+    return 0
+
+
+def del_model(args, parser):
+    """del_model, advntr_commands.py:218-223."""
+    from . import models
+    if not args.vntr_id:
+        _print_error(parser, '--vntr_id is required')
+    if args.models is None:
+        _print_error(parser, '--models is required')
+    models.delete_vntr_from_database(args.vntr_id, args.models)
+    return 0
+
+
+def add_model(args, parser):
+    """add_model, advntr_commands.py:179-215, for one locus or (--regions) many: every locus is set up, then all are trained
+    together (one GPU scan per chromosome, one scoring batch) and written in one transaction."""
+    from . import genome, settings, training
+    settings.ALIGN_REPEATS = bool(args.align_repeats)
+    if not args.reference:
+        _print_error(parser, '--reference is required')
+    if args.regions:
+        if args.chromosome or args.pattern or args.start is not None or args.end is not None:
+            _print_error(parser, '--regions does not go with --chromosome, --pattern, --start or --end')
+    else:
+        if not args.chromosome:
+            _print_error(parser, '--chromosome is required')
+        if not args.pattern:
+            _print_error(parser, '--pattern is required')
+        if not args.start:
+            _print_error(parser, '--start is required')
+        if not args.end:
+            _print_error(parser, '--end is required')
+    if args.models is None:
+        _print_error(parser, '--models is required')
+    try:
+        rows = training.parse_regions(args.regions) if args.regions else \
+            [(args.chromosome, args.start, args.end, args.pattern, "--chromosome %s --start %d --end %d --pattern %s"
+              % (args.chromosome, args.start, args.end, args.pattern))]
+        ref = genome.read_genome(args.reference)
+        sys.stderr.write("read %d records, %d bases from %s in %.2f s\n" % (len(ref.names()), ref.total_bases(),
+                                                                          args.reference, ref.seconds))
+        training.check_rows(rows, ref)
+    except (OSError, ValueError) as e:
+        raise SystemExit("ERROR: %s" % e)
+    print('Searching reference genome for regions with shared kmers with VNTR. It takes a few hours for human genome')
+    try:
+        vntrs = training.add_models(ref, rows, args.models)
+    except NotImplementedError as e:
+        raise SystemExit("ERROR: %s" % e)
+    for v in vntrs:
+        print('Training completed. VNTR saved with ID: %s to the database' % v.id)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m advntr_amd")
     sub = ap.add_subparsers(dest="cmd")
@@ -262,7 +354,38 @@ def main(argv=None):
                    help="search for a frameshift in the VNTR instead of a copy number (vntr_finder.py:256-309)")
     g.add_argument("--outfmt", choices=["text", "bed", "vcf"], default="text",
                    help="result rows as the reference writes them (genome_analyzer.py:28-170)")
+    a = sub.add_parser("addmodel", add_help=False,
+                       help="train a new locus (or every row of --regions) on a reference genome and add it to --models")
+    req, other = a.add_argument_group("Required arguments"), a.add_argument_group("Other options")
+    req.add_argument("-r", "--reference", help="reference genome (FASTA)")
+    req.add_argument("-c", "--chromosome", help="chromosome (e.g. chr1)")
+    req.add_argument("-p", "--pattern", help="first repeating pattern of the VNTR in forward (5' to 3') direction")
+    req.add_argument("-s", "--start", type=int, help="0-based start of the VNTR")
+    req.add_argument("-e", "--end", type=int, help="end of the VNTR")
+    req.add_argument("-m", "--models", help="sqlite model database (created when missing)")
+    other.add_argument("--regions", help="instead of -c/-p/-s/-e: a file of `chrom start end pattern` rows (0-based start); "
+                                         "ids follow the file order, all rows are written in one transaction")
+    other.add_argument("--align-repeats", action="store_true",
+                       help="align repeat units of unequal length with the built-in aligner (instead of refusing them)")
+    other.add_argument("-g", "--gene", help="accepted and stored as NULL, as the reference does")
+    other.add_argument("-a", "--annotation", help="accepted and stored as NULL, as the reference does")
+    other.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    d = sub.add_parser("delmodel", add_help=False, help="remove a locus from --models")
+    req, other = d.add_argument_group("Required arguments"), d.add_argument_group("Other options")
+    req.add_argument("-vid", "--vntr-id", "--vntr_id", dest="vntr_id", help="VNTR ID")
+    req.add_argument("-m", "--models", help="sqlite model database")
+    other.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    v = sub.add_parser("viewmodel", help="list the loci of --models")
+    v.add_argument("-g", "--gene", default="", help="comma-separated list of gene names")
+    v.add_argument("-p", "--pattern", help="repeating pattern of the VNTR in forward (5' to 3') direction")
+    v.add_argument("-m", "--models", help="sqlite model database")
     args = ap.parse_args(argv)
+    if args.cmd == "addmodel":
+        return add_model(args, a)
+    if args.cmd == "delmodel":
+        return del_model(args, d)
+    if args.cmd == "viewmodel":
+        return view_model(args, v)
     if args.cmd == "genotype":
         if not args.reads and not args.alignment:
             ap.error("genotype needs --reads and/or --alignment")

@@ -102,6 +102,8 @@ SYMBOLS = {
     "advntr_bam_spans_info": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "advntr_bam_spans_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "advntr_bam_spans_destroy": (None, [_vp]),
+    "advntr_genome_scan_host": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "advntr_genome_scan": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

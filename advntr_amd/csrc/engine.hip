@@ -1497,3 +1497,4 @@ extern "C" int advntr_host_threads(void) { return host_cpu_limit(); }
 #include "abi_comm.h"
 #include "abi_genotype.h"
 #include "abi_bam.h"
+#include "abi_genome_scan.h"

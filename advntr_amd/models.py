@@ -113,6 +113,19 @@ def save_reference_vntr_to_database(ref_vntr, db_file=None):
     db.close()
 
 
+def save_reference_vntrs_to_database(ref_vntrs, db_file=None):
+    """save_reference_vntr_to_database for many loci in one transaction: all rows are written or none."""
+    db = sqlite3.connect(_db_path(db_file))
+    try:
+        with db:
+            db.executemany("INSERT INTO vntrs(%s) VALUES(?,?,?,?,?,?,?,?,?,?,?)" % _COLUMNS,
+                           [(v.id, "True" if v.non_overlapping else "False", v.chromosome, v.start_point, v.gene_name,
+                             v.annotation, v.pattern, v.left_flanking_region, v.right_flanking_region,
+                             ','.join(v.get_repeat_segments()), v.scaled_score) for v in ref_vntrs])
+    finally:
+        db.close()
+
+
 def update_trained_score_in_database(vntr_id, scaled_recruitment_score, db_file=None):
     db = sqlite3.connect(_db_path(db_file))
     db.execute("UPDATE vntrs SET scaled_score=? WHERE id=?", (scaled_recruitment_score, vntr_id))

@@ -440,6 +440,22 @@ int advntr_bam_spans_fetch(const advntr_bam_spans *spans, int64_t *pairs, uint8_
                            uint8_t *unmapped_text, int64_t *unmapped_text_off);
 void advntr_bam_spans_destroy(advntr_bam_spans *spans);
 
+/* ---- False reads of new loci from a reference chromosome (addmodel training; csrc/genome_scan.h) ----
+ * For n_loci loci on one chromosome chrom[n] (FASTA bytes, any case): the reads VNTRFinder.simulate_false_filtered_reads
+ * makes for each, in its order, as [read_begin, read_end) spans of chrom (a Python slice, possibly empty).  Locus L has the
+ * VNTR [vntr_start[L], vntr_end[L]) and the keyword 11-mers kw[kw_off[L] .. kw_off[L+1]), 2 bits per base (A=0 C=1 G=2 T=3,
+ * first base highest).  read_begin / read_end hold ADVNTR_GENOME_SCAN_READS entries per locus; n_reads[L] are filled.   */
+#define ADVNTR_GENOME_SCAN_READS 10030  /* reads one locus can hold: 10 000 and then one more hit's 30                  */
+#define ADVNTR_GENOME_SCAN_STATS 7      /* upload ms, scan kernels ms, host fold ms, hits, chunks, bytes scanned, total ms */
+/* the rule on the host, position by position (the twin of the device pass)                                             */
+int advntr_genome_scan_host(const uint8_t *chrom, int64_t n, int32_t n_loci, const int64_t *vntr_start,
+                            const int64_t *vntr_end, const int32_t *kw_off, const uint32_t *kw, int64_t *read_begin,
+                            int64_t *read_end, int32_t *n_reads);
+/* the device pass: chunk = positions per chunk (0: the library's own; other values are for tests); stats may be NULL */
+int advntr_genome_scan(const uint8_t *chrom, int64_t n, int32_t n_loci, const int64_t *vntr_start, const int64_t *vntr_end,
+                       const int32_t *kw_off, const uint32_t *kw, int64_t chunk, int64_t *read_begin, int64_t *read_end,
+                       int32_t *n_reads, double *stats);
+
 #ifdef __cplusplus
 }
 #endif
