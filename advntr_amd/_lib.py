@@ -609,13 +609,16 @@ def viterbi_batch(models, bases, read_off, read_model, flags=0, want_paths=False
 
 
 def forward_batch(models, bases, read_off, read_model, flags=0):
+    """One-shot Model.log_probability from host buffers.  With FLAG_BOTH_STRANDS the arrays describe the forward reads and
+    the result holds 2n entries: entry n + i = the reverse complement of read i."""
     L = load()
-    n = len(read_off) - 1
+    n_in = len(read_off) - 1
     bases = np.ascontiguousarray(bases, np.uint8)
     read_off = np.ascontiguousarray(read_off, np.int64)
     read_model = np.ascontiguousarray(read_model, np.int32)
+    n = 2 * n_in if (flags & FLAG_BOTH_STRANDS) else n_in
     logp = np.zeros(n, np.float64)
-    check(L.advntr_forward_batch(_handles(models), len(models), ptr(bases), ptr(read_off), ptr(read_model), n,
+    check(L.advntr_forward_batch(_handles(models), len(models), ptr(bases), ptr(read_off), ptr(read_model), n_in,
                                  ptr(logp), flags))
     return logp
 

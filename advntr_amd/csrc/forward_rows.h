@@ -3,7 +3,9 @@
 // probabilities times 16^row (the class and emission tables are exponentiated in LDS when a model is staged, emissions
 // times the per-row scale 16; a sweep of at most 155 rows neither overflows nor underflows), the last row is captured
 // as scaled probabilities, taken back to the log domain after the sweep and handed to col_tail_forward.  No back-pointers,
-// no traceback.  Results agree with the reference's pair_lse folding to rounding (tests: 1e-9 relative; measured 3e-14).
+// no traceback.  Results agree with the reference's pair_lse folding to rounding: tests/test_gpu_forward.py holds every value
+// to tol() of tests/forward_exact.py (1e-13 + 64 u n + 16 u |logp| nats against a long-double forward; 1.7e-12 at 150 bases,
+// logp -300); measured: at most 0.07 of it.
 #pragma once
 #include "viterbi_rows.h"
 #include "forward_columns.h"
