@@ -94,20 +94,38 @@ def genotype(args):
         settings.MAX_ERROR_RATE = 0.3                                           # advntr_commands.py:66-71
         return finish(sharding.run_sharded([len(loc["pattern"]) for loc in loci],
                                            _pacbio_alignment_job(args, loci, seqs, row), comm))
+    measured = None
     if args.alignment:     # mapped reads are selected per locus, unmapped ones join --reads
-        from . import bam
+        from . import bam, coverage as coverage_mod
+        auto = bool(args.expansion) and args.coverage == "auto"
+        reference_genome = None
+        if auto and args.reference_filename:
+            from . import genome
+            try:
+                reference_genome = genome.read_genome(args.reference_filename)
+            except (OSError, ValueError) as e:
+                raise SystemExit("ERROR: %s" % e)
         kind = bam.sniff(args.alignment)
         if kind == "bgzf":     # BAM: one pass on the GPU keeps the records of the loci's windows and the unmapped ones
-            references = bam.read_header(args.alignment)[0]
-            samfile = bam.open_alignment(args.alignment, bam.vntr_windows(references, [loc["vntr"] for loc in loci]))
+            references, lengths, _ = bam.read_header(args.alignment)
+            if auto:           # a genome that does not fit the header is refused before the pass
+                _coverage_checked(coverage_mod.layout, references, lengths, reference_genome)
+            samfile = bam.open_alignment(args.alignment, bam.vntr_windows(references, [loc["vntr"] for loc in loci]),
+                                         coverage=auto, genome=reference_genome)
+            measured = samfile.coverage
         elif kind == "text":   # SAM text (`samtools view -h`)
             from . import sam_utils
             with open(args.alignment) as fh:
-                samfile = sam_utils.parse_sam(fh.read())
+                text = fh.read()
+            samfile = sam_utils.parse_sam(text)
+            if auto:           # the same rule on the host
+                measured = _coverage_checked(coverage_mod.measure_sam, samfile, coverage_mod.sam_reference_lengths(text),
+                                             reference_genome)
         else:
             raise SystemExit("%s: %s input is not supported (--alignment takes BAM or SAM text)" %
                              (args.alignment, "CRAM" if kind == "cram" else "gzip that is not BGZF"))
         seqs = seqs + [r.seq for r in samfile.reads if r.is_unmapped]
+    divisors = _expansion_divisors(args, loci, samfile, measured, rank)
     settings.MAX_ERROR_RATE = 0.3 if args.pacbio else 0.05                      # advntr_commands.py:66-71
     if args.pacbio:
         def pacbio_job(indices):
@@ -173,8 +191,8 @@ def genotype(args):
             picked, _ = vntr_finder.select_illumina_reads_multi([loci[i]["vntr"] for i in indices], samfile,
                                                                 [cands[i] for i in indices], models=built)
             return [row(loci[i], vntr_finder.find_repeat_count_from_selected_reads(
-                [s.summary for s in sel], accuracy_filter=args.accuracy_filter, is_haploid=args.haploid))
-                for i, sel in zip(indices, picked)]
+                [s.summary for s in sel], accuracy_filter=args.accuracy_filter, average_coverage=divisors[i],
+                is_haploid=args.haploid)) for i, sel in zip(indices, picked)]
         # scoring (both strands), recruit rule, selection and the per-locus aggregation + genotype without a Python object
         # per read: one engine batch, then advntr_genotype_illumina on the summary records
         results = vntr_finder.genotype_loci(built, [cands[i] for i in indices], [loci[i].get("scaled_score") for i in indices],
@@ -232,6 +250,48 @@ def _frameshift_row(loc, cand, read_length, hmm_utils, vntr_finder):
     result = vntr_finder.find_frameshift(model, len(loc["pattern"]), sum(len(x) for x in loc["repeat_segments"]), cand,
                                          loc.get("scaled_score"))
     return "%s\n%s\n" % (loc["id"], result)
+
+
+def _coverage_arg(text):
+    """-c: a float as the reference's type=float, or `auto`"""
+    if text == "auto":
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is neither a number nor `auto`" % text)
+
+
+def _coverage_checked(fn, *a):
+    """fn(*a), its ValueError (an alignment header and a genome that do not fit) as the command's error"""
+    try:
+        return fn(*a)
+    except ValueError as e:
+        raise SystemExit("ERROR: -c auto: %s" % e)
+
+
+def _expansion_divisors(args, loci, samfile, measured, rank):
+    """The average coverage to divide by, per locus: -c's value, or (-c auto) what was measured.  In auto mode rank 0 writes
+    one JSON line to stderr: where the divisor comes from, the sequencing mean, the windows, (windows, mean) per GC bin."""
+    if not args.expansion:
+        return [None] * len(loci)
+    if args.coverage != "auto":
+        return [args.coverage] * len(loci)
+    try:
+        out, empty = [], []
+        for loc in loci:
+            d, source = measured.divisor(loc["repeat_segments"])
+            out.append(d)
+            if source == "sequencing_mean_empty_bin":
+                empty.append(loc["id"])
+        summary = measured.summary()
+    except ValueError as e:
+        raise SystemExit("ERROR: -c auto: %s" % e)
+    if rank == 0:
+        for vid in empty:
+            sys.stderr.write("coverage: the GC bin of VNTR %s holds no window; its divisor is the sequencing mean\n" % vid)
+        sys.stderr.write(json.dumps({"coverage": summary}) + "\n")
+    return out
 
 
 def _print_error(parser, msg):
@@ -354,6 +414,16 @@ def main(argv=None):
                    help="search for a frameshift in the VNTR instead of a copy number (vntr_finder.py:256-309)")
     g.add_argument("--outfmt", choices=["text", "bed", "vcf"], default="text",
                    help="result rows as the reference writes them (genome_analyzer.py:28-170)")
+    g.add_argument("-e", "--expansion", action="store_true",
+                   help="with --alignment: estimate long expansions from PCR-free data as int(RU occurrences / (coverage x "
+                        "haplotypes)) for both alleles (vntr_finder.py:879-887); needs -c")
+    g.add_argument("-c", "--coverage", type=_coverage_arg, metavar="<float>|auto",
+                   help="with -e: average sequencing coverage (0 = the exact genotype), or `auto` to measure it from "
+                        "--alignment in the same pass (covered bases per 100-bp window on chr1-22, X, Y, windows above 200x "
+                        "left out; with -r the mean of the locus's GC bin, else the sequencing mean)")
+    g.add_argument("-r", "--reference-filename", "--reference_filename", dest="reference_filename", metavar="<file>",
+                   help="with -e -c auto: the reference genome (FASTA) the alignment was made against; windows are binned "
+                        "by its GC content (only uppercase G / C count, as the reference's get_gc_content)")
     a = sub.add_parser("addmodel", add_help=False,
                        help="train a new locus (or every row of --regions) on a reference genome and add it to --models")
     req, other = a.add_argument_group("Required arguments"), a.add_argument_group("Other options")
@@ -389,6 +459,13 @@ def main(argv=None):
     if args.cmd == "genotype":
         if not args.reads and not args.alignment:
             ap.error("genotype needs --reads and/or --alignment")
+        if args.expansion:
+            if args.coverage is None:
+                _print_error(g, 'Please specify the average coverage to identify the expansion')
+            if not args.alignment:
+                _print_error(g, '--expansion needs --alignment: the coverage method counts the reads of an alignment file')
+            if args.pacbio or args.frameshift:
+                _print_error(g, '--expansion does not go with %s' % ("--pacbio" if args.pacbio else "--frameshift"))
         if args.alignment and args.frameshift:
             ap.error("--alignment does not go with --frameshift")
         args.comm = None

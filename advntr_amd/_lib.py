@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("ADVNTR_HIP_LIB") or os.path.join(_HERE, "libadvntr_hi
 
 OK, ERR_ARG, ERR_SYMBOL, ERR_DEVICE, ERR_TOO_LARGE, ERR_UNSUPPORTED, ERR_DATA = 0, -1, -2, -3, -4, -5, -6
 BAM_RECORD_OFFSETS, BAM_FIELDS, BAM_STATS = 1, 10, 16
+BAM_COVERAGE, COVERAGE_BINS, BAM_COVERAGE_STATS = 2, 11, 6
 BAM_SPAN_FIELDS, BAM_SPAN_STATS = 10, 28
 FLAG_PATH, FLAG_FORCE_GENERIC, FLAG_NO_SUMMARY, FLAG_STREAM, FLAG_ANTIDIAGONAL, FLAG_BOTH_STRANDS = 1, 2, 4, 8, 16, 32
 FLAG_DEEP_TILES = 64
@@ -97,6 +98,13 @@ SYMBOLS = {
     "advntr_bam_kept_fetch": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "advntr_bam_kept_offsets": (ctypes.c_int, [_vp, _vp]),
     "advntr_bam_kept_destroy": (None, [_vp]),
+    "advntr_coverage_windows_host": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "advntr_coverage_gc_host": (ctypes.c_int, [_vp, _i64, _vp]),
+    "advntr_coverage_gc": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
+    "advntr_coverage_bins_host": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "advntr_bam_coverage_info": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "advntr_bam_coverage_windows": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
+    "advntr_bam_coverage_bins": (ctypes.c_int, [_vp, _i32, _vp, _i64, _vp, _vp]),
     "advntr_bam_span_host": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
     "advntr_bam_select_spans": (_vp, [ctypes.c_char_p, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _u32]),
     "advntr_bam_spans_info": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -146,6 +146,7 @@ class BamFile(object):
 
     def __init__(self, references, reads, windows, stats, offsets=None):
         self.references, self.reads, self.stats, self.offsets = references, reads, stats, offsets
+        self.coverage = None                # coverage.Coverage of a pass opened with coverage=True
         self._windows = {}
         for ref, s, e in windows:
             self._windows.setdefault(ref, []).append((int(s), int(e)))
@@ -168,12 +169,19 @@ class BamFile(object):
                 yield r
 
 
-def open_alignment(path, windows, chunk_bytes=0, record_offsets=False):
+def open_alignment(path, windows, chunk_bytes=0, record_offsets=False, coverage=False, genome=None, coverage_windows=False):
     """One pass over the BAM file at `path` on the device.  windows: (reference name, start, end) half-open, named as the
     file's references are (vntr_windows).  chunk_bytes: compressed bytes per streamed chunk (0 = 256 MiB).  With
-    record_offsets the uncompressed offset of every record is kept as well (tests)."""
+    record_offsets the uncompressed offset of every record is kept as well (tests).  With coverage the same pass sums the
+    covered bases per 100-bp window over every record (advntr_amd/coverage.py); the result's `coverage` is a
+    coverage.Coverage whose bins use the GC content of `genome` (genome.Genome) when one is given, and which holds the
+    per-window arrays of every reference when coverage_windows is set."""
     L = _lib.load()
-    references, _, _ = read_header(path)
+    references, lengths, _ = read_header(path)
+    lay = None
+    if coverage:
+        from . import coverage as coverage_mod
+        lay = coverage_mod.layout(references, lengths, genome)      # the errors of the layout before the pass
     index = {name: i for i, name in enumerate(references)}
     per_ref = [[] for _ in references]
     for ref, s, e in windows:
@@ -184,11 +192,12 @@ def open_alignment(path, windows, chunk_bytes=0, record_offsets=False):
     flat = [w for ws in per_ref for w in ws]
     ws = np.array([w[0] for w in flat] or [0], np.int64)
     we = np.array([w[1] for w in flat] or [0], np.int64)
-    h = L.advntr_bam_select(path.encode(), len(references), _lib.ptr(win_ptr), _lib.ptr(ws), _lib.ptr(we), int(chunk_bytes),
-                            _lib.BAM_RECORD_OFFSETS if record_offsets else 0)
+    flags = (_lib.BAM_RECORD_OFFSETS if record_offsets else 0) | (_lib.BAM_COVERAGE if coverage else 0)
+    h = L.advntr_bam_select(path.encode(), len(references), _lib.ptr(win_ptr), _lib.ptr(ws), _lib.ptr(we), int(chunk_bytes), flags)
     if not h:
         err = _lib.last_error()
         raise _lib.EngineError(_lib.ERR_DEVICE if "no HIP device" in err else _lib.ERR_DATA, err)
+    measured = None
     try:
         n_kept, text_bytes, n_offs = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         stats = np.zeros(_lib.BAM_STATS, np.float64)
@@ -202,12 +211,16 @@ def open_alignment(path, windows, chunk_bytes=0, record_offsets=False):
             offsets = np.zeros(max(1, n_offs.value), np.int64)
             _lib.check(L.advntr_bam_kept_offsets(h, _lib.ptr(offsets)))
             offsets = offsets[:n_offs.value]
+        if coverage:
+            measured = coverage_mod.measure_bam_handle(L, h, references, lay, genome is not None, coverage_windows)
     finally:
         L.advntr_bam_kept_destroy(h)
     reads = _reads(references, fields[:n_kept.value * _lib.BAM_FIELDS], text, toff)
     keys = ("blocks", "compressed_bytes", "uncompressed_bytes", "records", "kept", "chunks", "read_ms", "framing_ms",
             "upload_ms", "inflate_kernel_ms", "boundary_ms", "fallback_blocks", "fallback_ms", "select_ms", "total_ms")
-    return BamFile(references, reads, windows, dict(zip(keys, (float(x) for x in stats))), offsets)
+    out = BamFile(references, reads, windows, dict(zip(keys, (float(x) for x in stats))), offsets)
+    out.coverage = measured
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

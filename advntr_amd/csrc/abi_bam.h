@@ -6,6 +6,7 @@
 #include "bgzf_inflate.h"
 #include "bam_records.h"
 #include "bam_spans.h"
+#include "coverage_windows.h"
 
 namespace {
 
@@ -184,6 +185,18 @@ template <class T> struct DevBuf {       // a grow-only device buffer
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
+// the covered bases per window of an ADVNTR_BAM_COVERAGE pass (coverage_windows.h), resident on the device: reference r has
+// n_windows[r] = length / 100 full windows at slots base[r] .. base[r] + n_windows[r] of diff (one more slot: the sink).  diff
+// holds the difference arrays during the pass and every window's bp after the scan; zbits = the zero-length presence bits.
+struct BamCoverage {
+    bool on = false;
+    std::vector<int64_t> base, n_windows;
+    int64_t slots = 0;
+    DevBuf<int64_t> d_base, d_n_windows, d_diff, d_tile;
+    DevBuf<unsigned int> d_zbits;
+    double stats[ADVNTR_BAM_COVERAGE_STATS] = {0};
+};
+
 }  // namespace
 
 struct advntr_bam_kept {
@@ -192,6 +205,7 @@ struct advntr_bam_kept {
     std::vector<int64_t> text_off{0};
     std::vector<int64_t> offsets;
     double stats[ADVNTR_BAM_STATS] = {0};
+    BamCoverage cov;
 };
 
 extern "C" int advntr_bgzf_scan(const uint8_t *data, int64_t n_bytes, int64_t *block_off, int32_t *block_bytes, uint32_t *isize,
@@ -694,6 +708,66 @@ struct WholeDecode {
 
 }  // namespace
 
+namespace {
+
+// an ADVNTR_BAM_COVERAGE pass: the window layout from the header's lengths, the zeroed arrays, the events of the timings
+static int coverage_setup(const char *who, const char *path, int32_t n_ref, BamCoverage &C, hipEvent_t *ev)
+{
+    BamHeader H;
+    int rc = read_bam_header(path, H);
+    if (rc) return rc;
+    if ((int32_t)H.names.size() != n_ref) return fail(ADVNTR_ERR_ARG, "%s: %d window lists for %d references", who, n_ref, (int)H.names.size());
+    C.base.assign(n_ref, -1);
+    C.n_windows.assign(n_ref, 0);
+    C.slots = 0;
+    for (int32_t r = 0; r < n_ref; ++r) {
+        C.n_windows[r] = std::max<int64_t>(0, H.lengths[r]) / cov::WINDOW;
+        if (!C.n_windows[r]) continue;
+        C.base[r] = C.slots;
+        C.slots += C.n_windows[r] + 1;
+    }
+    const int64_t words = (C.slots + 31) / 32;
+    (void)current_device();
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&ev[i]));
+    if ((rc = C.d_base.ensure(std::max(n_ref, 1))) || (rc = C.d_n_windows.ensure(std::max(n_ref, 1))) ||
+        (rc = C.d_diff.ensure(std::max<int64_t>(1, C.slots))) || (rc = C.d_zbits.ensure(std::max<int64_t>(1, words))))
+        return rc;
+    if (n_ref) {
+        HIP_TRY(hipMemcpy(C.d_base.p, C.base.data(), n_ref * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(C.d_n_windows.p, C.n_windows.data(), n_ref * 8, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemset(C.d_diff.p, 0, std::max<int64_t>(1, C.slots) * 8));
+    HIP_TRY(hipMemset(C.d_zbits.p, 0, std::max<int64_t>(1, words) * 4));
+    HIP_TRY(hipStreamSynchronize(nullptr));         // the pass runs on non-blocking streams: the zeros land first
+    for (int32_t r = 0; r < n_ref; ++r) C.stats[5] += (double)C.n_windows[r];
+    C.on = true;
+    return ADVNTR_OK;
+}
+
+// after the last chunk: one inclusive scan over all references' slots turns the difference arrays into bp per window
+static int coverage_scan(BamCoverage &C, hipEvent_t *ev)
+{
+    if (!C.slots) return ADVNTR_OK;
+    const int64_t tiles = (C.slots + cov::SCAN_TILE - 1) / cov::SCAN_TILE;
+    int rc = C.d_tile.ensure(tiles);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ev[0], nullptr));
+    hipLaunchKernelGGL(cov::tile_sums_kernel, dim3((unsigned)tiles), dim3(cov::SCAN_THREADS), 0, nullptr, C.d_diff.p, C.slots, C.d_tile.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cov::tile_prefix_kernel, dim3(1), dim3(cov::SCAN_THREADS), 0, nullptr, C.d_tile.p, tiles);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cov::tile_scan_kernel, dim3((unsigned)tiles), dim3(cov::SCAN_THREADS), 0, nullptr, C.d_diff.p, C.slots, C.d_tile.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[1], nullptr));
+    HIP_TRY(hipEventSynchronize(ev[1]));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    C.stats[1] += ms;
+    return ADVNTR_OK;
+}
+
+}  // namespace
+
 extern "C" advntr_bam_kept *advntr_bam_select(const char *path, int32_t n_ref, const int32_t *win_ptr, const int64_t *win_start,
                                               const int64_t *win_end, int64_t chunk_bytes, uint32_t flags)
 {
@@ -713,10 +787,23 @@ extern "C" advntr_bam_kept *advntr_bam_select(const char *path, int32_t n_ref, c
     if (!n_ref) wp.assign(1, 0);
     std::vector<int64_t> h_kidx, h_kbytes;
     std::vector<std::pair<int64_t, int64_t>> kept;
+    BamCoverage &C = K->cov;
+    hipEvent_t ce[2] = {nullptr, nullptr};
+    struct Events {
+        hipEvent_t *e;
+        ~Events() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
+    } events_guard{ce};
     const ChunkFn select = [&](const uint8_t *d_buf, const int64_t *d_offs, int64_t n_rec, int64_t records_before, int64_t at,
                                hipStream_t s) -> int {
         int rc;
         if ((rc = d_kidx.ensure(n_rec)) || (rc = d_kbytes.ensure(n_rec))) return rc;
+        if (C.on) {         // the window accumulation of the same resident records, ahead of the selection on the same stream
+            HIP_TRY(hipEventRecord(ce[0], s));
+            hipLaunchKernelGGL(cov::accumulate_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, d_buf, d_offs, n_rec,
+                               n_ref, C.d_base.p, C.d_n_windows.p, (unsigned long long *)C.d_diff.p, C.d_zbits.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ce[1], s));
+        }
         const unsigned long long init[2] = {0, ~0ull};
         HIP_TRY(hipMemcpyAsync(d_counters.p, init, sizeof init, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(bam::select_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, s, d_buf, d_offs, n_rec,
@@ -726,6 +813,11 @@ extern "C" advntr_bam_kept *advntr_bam_select(const char *path, int32_t n_ref, c
         unsigned long long cnt[2];
         HIP_TRY(hipMemcpyAsync(cnt, d_counters.p, sizeof cnt, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
+        if (C.on) {
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ce[0], ce[1]));
+            C.stats[0] += ms;
+        }
         if (cnt[1] != ~0ull) return bad_record(path, d_offs, cnt[1], at);
         const int64_t nk = (int64_t)cnt[0];
         if (!nk) return ADVNTR_OK;
@@ -741,8 +833,10 @@ extern "C" advntr_bam_kept *advntr_bam_select(const char *path, int32_t n_ref, c
         (n_win && (hipMemcpy(d_ws.p, W.start.data(), n_win * 8, hipMemcpyHostToDevice) != hipSuccess ||
                    hipMemcpy(d_wmax.p, W.maxend.data(), n_win * 8, hipMemcpyHostToDevice) != hipSuccess)))
         return fail(ADVNTR_ERR_DEVICE, "advntr_bam_select: window upload failed"), nullptr;
+    if ((flags & ADVNTR_BAM_COVERAGE) && coverage_setup("advntr_bam_select", path, n_ref, C, ce)) return nullptr;
     if (bam_stream("advntr_bam_select", path, n_ref, chunk_bytes, flags & ADVNTR_BAM_RECORD_OFFSETS, K->offsets, K->stats, select))
         return nullptr;
+    if (C.on && coverage_scan(C, ce)) return nullptr;
     return K.release();
 }
 

@@ -1497,4 +1497,5 @@ extern "C" int advntr_host_threads(void) { return host_cpu_limit(); }
 #include "abi_comm.h"
 #include "abi_genotype.h"
 #include "abi_bam.h"
+#include "abi_coverage.h"
 #include "abi_genome_scan.h"

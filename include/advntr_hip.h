@@ -385,6 +385,7 @@ int advntr_bam_decode_host(const uint8_t *buf, int64_t n_bytes, const int64_t *o
  * [win_start[k], win_end[k]) for k in win_ptr[r] .. win_ptr[r+1]), and every unmapped (0x4) record.  Only those are
  * decoded.  flags: ADVNTR_BAM_RECORD_OFFSETS also keeps the uncompressed offset of every record.  NULL on error.    */
 #define ADVNTR_BAM_RECORD_OFFSETS 1u
+#define ADVNTR_BAM_COVERAGE 2u     /* also sum the covered bases per 100-bp window over every record (advntr_bam_coverage_*) */
 #define ADVNTR_BAM_FIELDS 10      /* refID, pos, flag, mapq, reference_end (-1 = None), name, seq, qual, cigar text lengths, 0 */
 #define ADVNTR_BAM_STATS 16       /* see advntr_bam_kept_info                                                             */
 advntr_bam_kept *advntr_bam_select(const char *path, int32_t n_ref, const int32_t *win_ptr, const int64_t *win_start,
@@ -398,6 +399,38 @@ int advntr_bam_kept_info(const advntr_bam_kept *kept, int64_t *n_kept, int64_t *
 int advntr_bam_kept_fetch(const advntr_bam_kept *kept, int32_t *fields, uint8_t *text, int64_t *text_off);
 int advntr_bam_kept_offsets(const advntr_bam_kept *kept, int64_t *offsets);
 void advntr_bam_kept_destroy(advntr_bam_kept *kept);
+
+/* ---- Coverage per 100-bp reference window (CoverageBiasDetector / CoverageCorrector, advntr/coverage_bias.py; the rule is
+ * written down in csrc/coverage_windows.h) ----
+ * An interval [start, end) adds its overlap in bp to every window [100w, 100w + 100) it reaches and makes it present (a
+ * zero-length interval makes its own window present with 0 bp); only the length / 100 full windows of a reference exist.  A
+ * present window with bp <= 20000 (coverage <= 200) enters GC bin gc / 10, gc = the uppercase G and C bytes of its 100
+ * reference bases; per bin, the count of windows and the sum of their bp.  Exact integers throughout.                  */
+#define ADVNTR_COVERAGE_BINS 11
+#define ADVNTR_BAM_COVERAGE_STATS 6  /* accumulate kernel ms, scan kernels ms, chromosome upload ms, GC kernel ms, bins kernel ms,
+                                      * windows                                                                           */
+/* the accumulation on the host: reference r has n_windows[r] windows, at bp / present[sum(n_windows[0 .. r))]; record i is
+ * the interval [rec_start[i], rec_end[i]) of reference rec_ref[i] (skipped when rec_ref is outside 0 .. n_ref - 1 or
+ * rec_start is negative)                                                                                                */
+int advntr_coverage_windows_host(int32_t n_ref, const int64_t *n_windows, const int32_t *rec_ref, const int64_t *rec_start,
+                                 const int64_t *rec_end, int64_t n_rec, int64_t *bp, uint8_t *present);
+/* GC counts of the n / 100 full windows of chrom[n] (FASTA bytes as they are: only uppercase G and C count), on the host  */
+int advntr_coverage_gc_host(const uint8_t *chrom, int64_t n, uint8_t *gc);
+/* the same on the device; ms (may be NULL) receives the upload and kernel milliseconds                                 */
+int advntr_coverage_gc(const uint8_t *chrom, int64_t n, uint8_t *gc, double *ms);
+/* bins of n_windows windows on the host: bin_windows / bin_bp[ADVNTR_COVERAGE_BINS] are added to; gc NULL = all in bin 0 */
+int advntr_coverage_bins_host(const int64_t *bp, const uint8_t *present, const uint8_t *gc, int64_t n_windows,
+                              int64_t *bin_windows, int64_t *bin_bp);
+/* of an advntr_bam_select pass made with ADVNTR_BAM_COVERAGE: every record (any flag; refID -1 and negative POS skipped) is
+ * the interval [pos, CIGAR reference end) when mapped with a CIGAR, else [pos, pos + l_seq), summed on the device into the
+ * windows of its reference (length from the BAM header).  *n_ref and n_windows[n_ref] (may be NULL); stats[ADVNTR_BAM_COVERAGE_STATS] */
+int advntr_bam_coverage_info(const advntr_bam_kept *kept, int32_t *n_ref, int64_t *n_windows, double *stats);
+/* the windows of reference `ref`: bp[n_windows[ref]] and present[n_windows[ref]] (0 / 1)                              */
+int advntr_bam_coverage_windows(const advntr_bam_kept *kept, int32_t ref, int64_t *bp, uint8_t *present);
+/* the bins of reference `ref` on the device, added to bin_windows / bin_bp[ADVNTR_COVERAGE_BINS]: chrom[chrom_len] = its
+ * reference sequence (GC counted on the device; chrom_len / 100 must equal its window count), or NULL = all in bin 0    */
+int advntr_bam_coverage_bins(advntr_bam_kept *kept, int32_t ref, const uint8_t *chrom, int64_t chrom_len, int64_t *bin_windows,
+                             int64_t *bin_bp);
 
 /* ---- Long reads of an aligned BAM (VNTRFinder.find_repeat_count_from_pacbio_alignment_file, vntr_finder.py:640-651) --
  * For a mapped record and a VNTR window [vs, ve) (flank F, minimum flank MIN; the reference's 100 and 10): aligned bases are
